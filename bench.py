@@ -1,6 +1,20 @@
 """Benchmark of the hot path: L=4096 Villain NeighborhoodUpdate sweeps (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--L 4096]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--L 4096] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and nothing else: set up, warm up, time the K steps, write the
+outputs if --dump-outputs is given, print the result line.  --full adds the measurements that take runs of their
+own: the CPU baseline (cpu_baseline), the measured copy-kernel HBM ceiling (roofline.copy_ceiling_GBps), the
+tile-alone and single-lattice rates of a domain line (config.scaling_reference), and a second timed window for the
+kernel time when the first one held no countable launch.  Without it those fields are null.
+
+--dump-outputs DIR (the N = 1 headline workload): after the timed steps, DIR/phi.npy and DIR/n.npy hold the fields
+the timed path left after its last step (float64; for a lattice of more than 2^21 sites the same fixed, seeded sample
+of 2^21 sites of each, dump_sample() below), and DIR/accepted.npy the accepted proposals of each timed step.  The
+timed steps of such a run start from a state that depends on the arguments alone (cold start, seed 0, then exactly
+W warm-up steps: the time-based warm-up of --warmup-s runs before that state is set up), so two runs with the same
+arguments write the same arrays.  (Without the option the --warmup-s steps, as many as the clock allows, run on
+the timed chain itself, after the W steps.)
 
 A "step" is one NeighborhoodUpdate sweep (neighborhood.py:59-137) of the whole lattice, in the
 reference's own chain semantics (NumPy PCG64 stream replayed on the device, bit-exact parity mode),
@@ -13,8 +27,8 @@ with the fields resident in HBM.
          with RCCL halo exchanges (strong scaling; the chain is bit-identical to the 1-GPU chain).  --weak: an
          L x L tile per GPU of a (ty L) x (tx L) lattice instead (north_star's weak-scaling efficiency), and the
          metric names that lattice.  --tiles TYxTX on one GPU emulates a decomposition.
-         Every domain line also carries, under config.scaling_reference, rates timed after the same warm-up as
-         the main run (warm_up: W steps, then --warmup-s seconds) over max(--steps, 100) sweeps: R1 = this rank's
+         With --full every domain line also carries, under config.scaling_reference, rates timed after the same
+         warm-up as the main run (warm_up: W steps, then --warmup-s seconds) over max(--steps, 100) sweeps: R1 = this rank's
          tile alone as a periodic lattice (E_N = R_N / (N R1)), and the single-lattice headline
          path on one L x L lattice (the N = 1 line's kernel: for --weak the per-GPU R1, for strong the 1-GPU
          rate of the whole problem).  An E_N above 1.02 is flagged (E_N_suspect) and printed to stderr.
@@ -80,7 +94,13 @@ def parse():
     ap.add_argument('--rng', default='pcg64', choices=['pcg64', 'philox'],
                     help='villain workload: pcg64 = the reference chain (NumPy stream replay, the headline); philox = '
                          'the optional counter-based mode (SURVEY.md 8(b) sv_rng mode 1, a different chain)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the CPU baseline, the copy-kernel HBM '
+                         'ceiling, a domain line\'s scaling_reference rates (off by default)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='headline workload: write the fields after the last timed step (a fixed sample of them '
+                         'above 2^21 sites) and the accepted counts of the timed steps as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-sweeps', type=int, default=5)
     ap.add_argument('--weak', action='store_true', help='an L x L tile per GPU of a (ty L) x (tx L) lattice (weak '
                                                         'scaling; with --tiles on one GPU, emulate that layout); the '
@@ -90,7 +110,8 @@ def parse():
     ap.add_argument('--warmup-s', type=float, default=1.0,
                     help='after the W warmup steps, keep warming (untimed) until this many seconds have passed: '
                          'clocks and page mappings reach steady state before the timed region')
-    ap.add_argument('--no-copy-ceiling', action='store_true', help='skip the measured copy-kernel HBM ceiling')
+    ap.add_argument('--no-copy-ceiling', action='store_true',
+                    help='with --full: skip the measured copy-kernel HBM ceiling')
     ap.add_argument('--tiles', default=None, help='tile grid TYxTX (default from N); with N=1 emulates the '
                                                    'decomposition on one GPU')
     ap.add_argument('--transport', default='rccl', choices=['rccl', 'host'],
@@ -111,6 +132,8 @@ def parse():
     args = ap.parse_args()
     if args.strong and args.weak:
         ap.error('--strong and --weak exclude each other')
+    if args.dump_outputs and (args.workload != 'villain' or args.tiles or (args.gpus or 1) > 1):
+        ap.error('--dump-outputs is implemented for the N = 1 headline workload only')
     # BASELINE config 4 (one L x L lattice over the GPUs, strong scaling) unless --weak
     args.strong = not args.weak
     if args.workload in ('replicas', 'worms'):
@@ -156,9 +179,19 @@ def cpu_baseline(L, kappa, W, sweeps):
                       '1 core (the sequential restatement: value_1core)'}
 
 
-def warm_up(run, args, dist=None):
+def warm_up(run, args, dist=None, reset=None):
     """Untimed warmup: the W steps the driver asks for, then more until --warmup-s seconds have passed (GPU
-    clocks and page mappings at steady state).  Collective runs agree on the extra step count (max over ranks)."""
+    clocks and page mappings at steady state).  Collective runs agree on the extra step count (max over ranks).
+    With `reset` (a callable that puts the chain back to its start) the time-based part runs first, then reset(),
+    then the W steps: the timed steps then start from the same state in every run, however many steps the clock
+    allowed."""
+    if reset is not None:
+        if args.warmup_s > 0:
+            warm_up(run, argparse.Namespace(warmup=1, warmup_s=args.warmup_s), dist)
+        reset()
+        if args.warmup:
+            run(args.warmup)
+        return
     t0 = time.perf_counter()
     if args.warmup:
         run(args.warmup)
@@ -183,6 +216,32 @@ def copy_ceiling(ctx):
     if _native.lib().sv_hbm_copy(ctx.handle, 1 << 30, 16, 20, ctypes.byref(g)) != 0:
         return None
     return g.value
+
+
+DUMP_SITES = 1 << 21  # --dump-outputs: sites written per field (phi 16 MiB + n 32 MiB: under 64 MB in all)
+
+
+def dump_sample(sites):
+    """Sorted flat site indices of the --dump-outputs sample: every site up to DUMP_SITES, else DUMP_SITES of them
+    drawn without replacement from a fixed seed (the same in every run and build)."""
+    if sites <= DUMP_SITES:
+        return np.arange(sites)
+    return np.sort(np.random.default_rng(20240607).choice(sites, size=DUMP_SITES, replace=False))
+
+
+def dump_outputs(path, ctx, Lib, h, L, st, steps):
+    """Write what the timed call returned to its caller: the fields after its last step (downloaded from the
+    device; float64, n's int64 values are exact in it) and the accepted count of each timed step."""
+    from supervillain_amd import _native
+    phi = np.empty((L, L))
+    n = np.empty((2, L, L), dtype=np.int64)
+    ctx.check(Lib.sv_villain_download(h, _native.ptr(phi), _native.ptr(n)), 'sv_villain_download')
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample(L * L)
+    whole = idx.size == L * L
+    np.save(os.path.join(path, 'phi.npy'), phi if whole else phi.reshape(-1)[idx])
+    np.save(os.path.join(path, 'n.npy'), (n if whole else n.reshape(2, -1)[:, idx]).astype(np.float64))
+    np.save(os.path.join(path, 'accepted.npy'), np.array([st[i].accepted for i in range(steps)], dtype=np.float64))
 
 
 def max_over_ranks(dist, x):
@@ -244,7 +303,8 @@ def report(args, world, sites_per_step, sites_per_launch, elapsed, acc, avg_laun
     if lat is not None and named is not None and tuple(lat) != named:
         raise ValueError(f'bench.py: the metric names a {named[0]}x{named[1]} lattice but the run swept '
                          f'{lat[0]}x{lat[1]}: {metric}')
-    ceiling = copy_ceiling(ctx) if ctx is not None and not getattr(args, 'no_copy_ceiling', False) else None
+    full = getattr(args, 'full', False)  # the legs below are runs of their own: --full only
+    ceiling = copy_ceiling(ctx) if full and ctx is not None and not getattr(args, 'no_copy_ceiling', False) else None
     out = {
         'metric': metric,
         'value': args.steps * sites_per_step / elapsed,
@@ -276,7 +336,7 @@ def report(args, world, sites_per_step, sites_per_launch, elapsed, acc, avg_laun
                      'frac_of_copy_ceiling': achieved / ceiling if ceiling else None},
         'cpu_baseline': None,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = (baseline or (lambda: cpu_baseline(args.L, args.kappa, args.W, args.cpu_sweeps)))()
     print(json.dumps(out), flush=True)
 
@@ -441,12 +501,14 @@ def run_worldline_domain(args, world, rank, dist):
     rej = sum(s.rejections for s in st)
     ctx = dom.ctx
     dom.close()
-    one = WorldlineDomain(Ht, Wt, (1, 1), **kw)
-    one.cold()
-    g1 = np.random.default_rng(1)
-    r1, _ = timed_rate(lambda k: one.run(k, g1), Ht * Wt, args, dist)
-    one.close()
-    r1_mean = r1 if dist is None else _mean_over_ranks(dist, r1)
+    r1_mean = None
+    if args.full:
+        one = WorldlineDomain(Ht, Wt, (1, 1), **kw)
+        one.cold()
+        g1 = np.random.default_rng(1)
+        r1, _ = timed_rate(lambda k: one.run(k, g1), Ht * Wt, args, dist)
+        one.close()
+        r1_mean = r1 if dist is None else _mean_over_ranks(dist, r1)
     if rank == 0:
         value = args.steps * Nt * Nx / elapsed
         config = {'workload': f'{Nt}x{Nx} Worldline: checkerboard PlaquetteUpdate + CoexactUpdate sweep per step, '
@@ -456,7 +518,8 @@ def run_worldline_domain(args, world, rank, dist):
                   'halo_transport': args.transport if world > 1 else 'none (one process)',
                   'parallelism': f'{ty}x{tx} domain decomposition over {world} GPU(s)',
                   'lemire_rejections_in_timed_steps': int(rej),
-                  'scaling_reference': scaling_reference(value, world, r1_mean, [Ht, Wt], None, None, 'steps')}
+                  'scaling_reference': (scaling_reference(value, world, r1_mean, [Ht, Wt], None, None, 'steps')
+                                        if args.full else None)}
         report(args, world, Nt * Nx, Nt * Nx // world, elapsed, acc, avg_launch_s, config, Ht,
                metric=lattice_metric(Nt, Nx, 'Worldline', None if args.strong else [Ht, Wt],
                                      head='plaquette-steps/sec (Plaquette + Coexact sweep)', tail=f', W={args.W}'),
@@ -770,15 +833,16 @@ def run_domain(args, world, rank, local, dist):
     dom.close()
 
     # R1: this rank's tile alone, as a periodic Ht x Wt lattice on its own GPU, no exchange, timed
-    # after the same warm-up as the main run; then the single-lattice headline path on one L x L lattice
-    one = VillainDomain(Ht, Wt, (1, 1), **kw)
-    one.cold()
-    g1 = np.random.default_rng(1)
-    r1, _ = timed_rate(lambda k: one.run(k, g1), Ht * Wt, args, dist)
-    one.close()
-    r1_mean = r1 if dist is None else _mean_over_ranks(dist, r1)
-    single, single_rej = single_lattice_rate(L, args, dist)
-    single_mean = single if dist is None else _mean_over_ranks(dist, single)
+    # after the same warm-up as the main run; then the single-lattice headline path on one L x L lattice (--full)
+    if args.full:
+        one = VillainDomain(Ht, Wt, (1, 1), **kw)
+        one.cold()
+        g1 = np.random.default_rng(1)
+        r1, _ = timed_rate(lambda k: one.run(k, g1), Ht * Wt, args, dist)
+        one.close()
+        r1_mean = r1 if dist is None else _mean_over_ranks(dist, r1)
+        single, single_rej = single_lattice_rate(L, args, dist)
+        single_mean = single if dist is None else _mean_over_ranks(dist, single)
 
     if rank == 0:
         value = args.steps * Nt * Nx / elapsed
@@ -792,7 +856,8 @@ def run_domain(args, world, rank, local, dist):
                   'parallelism': f'{ty}x{tx} domain decomposition over {world} GPU(s)' +
                                  ('' if world > 1 else ' (emulated: every tile on this GPU in turn)'),
                   'lemire_rejections_in_timed_steps': int(rej),
-                  'scaling_reference': scaling_reference(value, world, r1_mean, [Ht, Wt], single_mean, int(single_rej))}
+                  'scaling_reference': (scaling_reference(value, world, r1_mean, [Ht, Wt], single_mean, int(single_rej))
+                                        if args.full else None)}
         report(args, world, Nt * Nx, Nt * Nx // world, elapsed, acc, avg_launch_s, config, Ht, ctx=ctx,
                metric=lattice_metric(Nt, Nx, weak_tile=None if args.strong else [Ht, Wt]),
                kernel='villain_sweep_hot (tile)')
@@ -879,9 +944,16 @@ def main():
     phi = np.zeros((L, L))
     n = np.zeros((2, L, L), dtype=np.int64)
     ctx.check(Lib.sv_villain_upload(h, _native.ptr(phi), _native.ptr(n)), 'upload')
-    r = rng_from_numpy(np.random.default_rng(0))
     from supervillain_amd._abi import SvPhilox
+    r = rng_from_numpy(np.random.default_rng(0))
     ph = SvPhilox(0x5eed, 0, 0)
+
+    def reset():
+        """Back to the start of the chain: the cold fields on the device, both generators at their seeds."""
+        nonlocal r, ph
+        ctx.check(Lib.sv_villain_upload(h, _native.ptr(phi), _native.ptr(n)), 'upload')
+        r = rng_from_numpy(np.random.default_rng(0))
+        ph = SvPhilox(0x5eed, 0, 0)
 
     def run(k):
         st = _native.stats_array(k)
@@ -893,7 +965,9 @@ def main():
                       'sv_villain_run')
         return st
 
-    warm_up(run, args)
+    # (a dump asks for the same timed window in every run; a plain run needs no second upload and keeps warming the
+    # chain it times)
+    warm_up(run, args, reset=reset if args.dump_outputs else None)
     Lib.sv_ctx_set_timing(ctx.handle, 2 if args.event_timing == 'launch' else 1)
     Lib.sv_ctx_block_counts(ctx.handle, None, None)  # (reset: count the timed sweeps' kernels only)
     Lib.sv_ctx_band_counts(ctx.handle, None, None)
@@ -902,10 +976,13 @@ def main():
     t1 = time.perf_counter()
     # hipEvents around the hot kernel's launches in the timed region (replays of a sweep that met a NumPy Lemire
     # rejection run on the general kernel and are not counted); if the window held no countable launch (a
-    # rejection in its last sweep), time the next `steps` sweeps the same way, after the timed region
+    # rejection in its last sweep), --full times the next `steps` sweeps the same way, after the timed region
+    # (a plain run's roofline then falls back to the wall clock per step, launch_time_source)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, Lib, h, L, st, args.steps)
     launches = ctypes.c_int64()
     Lib.sv_ctx_kernel_time(ctx.handle, None, ctypes.byref(launches))
-    if launches.value == 0:
+    if launches.value == 0 and args.full:
         run(args.steps)
     avg_launch_s = kernel_time(Lib, ctx)
     acc = sum(st[i].accepted for i in range(args.steps)) / (args.steps * L * L)

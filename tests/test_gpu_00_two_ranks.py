@@ -166,7 +166,7 @@ def test_bench_two_ranks_hosted(workload):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SV_DEVICE='0', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--transport', 'host', '--steps', '4',
-           '--warmup', '1', '--warmup-s', '0', '--no-cpu-baseline', '--no-copy-ceiling', '--L', '512',
+           '--warmup', '1', '--warmup-s', '0', '--full', '--no-cpu-baseline', '--no-copy-ceiling', '--L', '512',
            '--workload', workload]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -196,12 +196,12 @@ def test_rng_batch_roundtrip():
 
 def test_bench_json_contract(capsys):
     """bench.py's report line carries every field the driver and the judge read (CPU-only: synthetic timings,
-    the CPU baseline on a small lattice)."""
+    the CPU baseline of a --full run on a small lattice)."""
     import json
     import types
     import bench
     args = types.SimpleNamespace(steps=10, warmup=2, strong=False, no_cpu_baseline=False, L=64, kappa=0.5, W=1,
-                                 cpu_sweeps=2)
+                                 cpu_sweeps=2, full=True)
     bench.report(args, 1, 4096 * 4096, 4096 * 4096, 3.2e-3, 0.004, 3.2e-4,
                  {'workload': 'L=4096 test', 'L': 4096, 'parallelism': 'single GPU'}, 4096)
     d = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
@@ -215,6 +215,40 @@ def test_bench_json_contract(capsys):
     c = d['cpu_baseline']
     assert c['cores'] >= 1 and c['kind'] == 'port' and c['value'] > 0 and c['value_1core'] > 0
     assert abs(d['value'] - 10 * 4096 * 4096 / 3.2e-3) < 1e-3 * d['value']
+
+
+def test_bench_plain_run_skips_the_extra_legs(capsys, monkeypatch):
+    """Without --full the report runs neither the CPU baseline nor the copy ceiling (both null, the headline fields
+    unchanged), --full and --dump-outputs parse, and the dump's site sample is fixed."""
+    import json
+    import sys
+    import types
+    import bench
+    monkeypatch.setattr(bench, 'cpu_baseline', lambda *a: pytest.fail('the CPU baseline ran in a plain run'))
+    monkeypatch.setattr(bench, 'copy_ceiling', lambda *a: pytest.fail('the copy ceiling ran in a plain run'))
+    args = types.SimpleNamespace(steps=10, warmup=2, strong=True, no_cpu_baseline=False, L=64, kappa=0.5, W=1,
+                                 cpu_sweeps=2, full=False)
+    bench.report(args, 1, 4096 * 4096, 4096 * 4096, 3.2e-3, 0.004, 3.2e-4,
+                 {'workload': 'L=4096 test', 'L': 4096, 'parallelism': 'single GPU'}, 4096, ctx=object())
+    d = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert d['cpu_baseline'] is None and d['roofline']['copy_ceiling_GBps'] is None
+    assert d['metric'] == bench.HEADLINE_METRIC and d['unit'] == 'lattice-site updates/s' and d['dtype'] == 'f64+int64'
+    assert d['higher_is_better'] is True and abs(d['ms_per_step'] - 0.32) < 1e-12
+    assert abs(d['value'] - 10 * 4096 * 4096 / 3.2e-3) < 1e-3 * d['value']
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '3'])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--full', '--dump-outputs', 'somewhere'])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == 'somewhere'
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--workload', 'replicas', '--dump-outputs', 'somewhere'])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    capsys.readouterr()
+    s = bench.dump_sample(4096 * 4096)
+    assert s.size == bench.DUMP_SITES and (np.diff(s) > 0).all() and 0 <= s[0] and s[-1] < 4096 * 4096
+    assert (s == bench.dump_sample(4096 * 4096)).all() and (bench.dump_sample(100) == np.arange(100)).all()
+    assert bench.DUMP_SITES * 8 * 3 < 64e6  # phi and the two components of n, float64
 
 
 def test_bench_metric_names_the_lattice(capsys, monkeypatch):
