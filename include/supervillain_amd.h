@@ -358,6 +358,39 @@ int sv_worldline_worm_batch(sv_ctx *ctx, int32_t R, int32_t N, double kappa, dou
                             int32_t v_is_float, int32_t worms, int64_t max_moves, sv_rng *rngs, int64_t *hist,
                             int64_t *lengths);
 
+/* ---- Two-point functions: Spin_Spin and Vortex_Vortex of both formulations ------------------------------
+ * None of these changes a state or touches an rng; they run on the context's stream, after the sweeps queued
+ * there.  Outputs are indexed [dt mod N, dx mod N] like the reference's.  A size a path does not serve returns
+ * -2 with a message that starts "not implemented" (NotImplementedError in Python).
+ *
+ * The direct pair: one cross-correlation C(r) = 1/V sum_x conj f(x) f(x - r) (Lattice.correlation,
+ * supervillain/lattice/compact.py:465-...; there np.fft) of a field formed on the device; out is N*N complex128
+ * (interleaved).  path: 0 auto, 1 direct sum (any N >= 2 with N*N <= 2^16), 2 FFT (N a power of two, 4..4096). */
+/* Replaces Spin_Spin.Villain, supervillain/observable/spin.py:28-42: f = exp(i phi). */
+int sv_villain_spin_spin(sv_villain *st, double *out, int32_t path);
+/* Replaces Vortex_Vortex.Worldline, supervillain/observable/vortex.py:22-37 (D = 2: one orientation):
+ * f = exp(2 pi i v / W_eff). */
+int sv_worldline_vortex_vortex(sv_worldline *st, double W_eff, double *out, int32_t path);
+/* The taxicab pair: per displacement, the mean over all origins of the reweighting factor along the fixed
+ * time-then-space path, from periodic prefix sums of the links; out is N*N float64, out[0] = 1;
+ * 2 <= N <= 2048. */
+/* Replaces Vortex_Vortex.Villain, supervillain/observable/vortex.py:63-189, on Links.Villain = d(phi) - 2 pi n
+ * (observable/links.py:17-31), formed on the device. */
+int sv_villain_vortex_vortex(sv_villain *st, double kappa, double *out);
+/* Replaces Spin_Spin.Worldline, supervillain/observable/spin.py:50-224, on Links.Worldline = m - delta(v) / W_eff
+ * (links.py:35-45), formed on the device; for integer v and W the link sums are exact integers, divided once. */
+int sv_worldline_spin_spin(sv_worldline *st, double kappa, double W_eff, double *out);
+/* One-shot forms on host arrays, the reference's own signatures.  sv_correlation: Lattice.correlation(f, f)
+ * (compact.py:465-...) of a complex128 field f (N*N, interleaved). */
+int sv_correlation(sv_ctx *ctx, int32_t N, const double *f, double *out, int32_t path);
+/* out[dt, dx] = 1/V sum over origins of exp(a s + b (|dt| + |dx|)), s the signed sum of the float64 links (2, N, N)
+ * over the path: dual = 0 the path of spin.py:158-190 (a = -1/kappa, b = -1/(2 kappa)), dual = 1 the dual path of
+ * vortex.py:161-175 (a = 2 pi kappa, b = -2 pi^2 kappa). */
+int sv_taxicab_correlator(sv_ctx *ctx, int32_t N, const double *links, double a, double b, int32_t dual, double *out);
+/* Diagnostic (tests): the taxicab kernel sums the origins in units fixed by N; a workgroup takes `units_per_group`
+ * of them (0: the default, 1).  The setting changes the launch geometry and no result. */
+int sv_ctx_set_taxicab_units(sv_ctx *ctx, int32_t units_per_group);
+
 #ifdef __cplusplus
 }
 #endif

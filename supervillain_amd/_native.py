@@ -134,6 +134,13 @@ def lib():
         L.sv_replicas_worm_run.argtypes = [vp, f64, i64, i32, i64, vp, vp, vp]
         L.sv_worldline_worm_run.argtypes = [vp, f64, f64, i32, i64, P(SvRng), vp, vp]
         L.sv_worldline_worm_batch.argtypes = [vp, i32, i32, f64, f64, vp, vp, i32, i32, i64, vp, vp, vp]
+        L.sv_villain_spin_spin.argtypes = [vp, vp, i32]
+        L.sv_worldline_vortex_vortex.argtypes = [vp, f64, vp, i32]
+        L.sv_villain_vortex_vortex.argtypes = [vp, f64, vp]
+        L.sv_worldline_spin_spin.argtypes = [vp, f64, f64, vp]
+        L.sv_correlation.argtypes = [vp, i32, vp, vp, i32]
+        L.sv_taxicab_correlator.argtypes = [vp, i32, vp, f64, f64, i32, vp]
+        L.sv_ctx_set_taxicab_units.argtypes = [vp, i32]
         _LIB = L
         return L
 
@@ -157,7 +164,9 @@ EXPORTED = ('sv_ctx_create', 'sv_ctx_destroy', 'sv_last_error', 'sv_device_count
             'sv_domain_exchange_plan_worldline', 'sv_domain_message_layout_worldline',
             'sv_replicas_create', 'sv_replicas_destroy', 'sv_replicas_upload', 'sv_replicas_download',
             'sv_replicas_run', 'sv_replicas_run_measured', 'sv_replicas_villain', 'sv_villain_worm_run', 'sv_replicas_worm_run', 'sv_worldline_worm_run',
-            'sv_worldline_worm_batch')
+            'sv_worldline_worm_batch',
+            'sv_villain_spin_spin', 'sv_worldline_vortex_vortex', 'sv_villain_vortex_vortex', 'sv_worldline_spin_spin',
+            'sv_correlation', 'sv_taxicab_correlator', 'sv_ctx_set_taxicab_units')
 
 
 def default_device():

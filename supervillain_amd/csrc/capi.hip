@@ -603,6 +603,7 @@ int sv_ctx_destroy(sv_ctx *ctx) {
     (void)hipFree(ctx->d_skips);
     (void)hipFree(ctx->d_stats);
     sv::worm_release(ctx);
+    sv::correlators_release(ctx);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return e == hipSuccess ? 0 : -2;  // (the context is gone: the caller learns only that its last work failed)

@@ -232,6 +232,7 @@ namespace sv {
 void villain_worms_device(sv_ctx *ctx, int32_t R, int32_t N, const double *phi, int64_t *n, double kappa, int64_t W,
                           int32_t worms, int64_t max_moves, sv_rng *rngs, int64_t *hist, int64_t *lengths);
 void worm_release(sv_ctx *ctx);  // frees the context's worm scratch (sv_ctx_destroy)
+void correlators_release(sv_ctx *ctx);  // correlators.hip: frees the context's correlator work buffers (sv_ctx_destroy)
 }  // namespace sv
 
 struct sv_worldline {

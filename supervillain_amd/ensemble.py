@@ -10,6 +10,7 @@ import time
 
 import numpy as np
 
+from supervillain_amd import observable
 from supervillain_amd.batch import Batch
 from supervillain_amd.configurations import Configurations
 from supervillain_amd.generator.combining import KeepEvery
@@ -185,6 +186,9 @@ class Ensemble:
     def __getattr__(self, name):
         if name == 'configuration':
             raise AttributeError(name)
+        if name in observable.registry and 'Action' in self.__dict__:
+            # an observable (observable/observable.py:36-93): inline column, or measured per configuration and cached
+            return observable.measure(self, name)
         return getattr(self.configuration, name)
 
 
