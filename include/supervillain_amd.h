@@ -391,6 +391,44 @@ int sv_taxicab_correlator(sv_ctx *ctx, int32_t N, const double *links, double a,
  * of them (0: the default, 1).  The setting changes the launch geometry and no result. */
 int sv_ctx_set_taxicab_units(sv_ctx *ctx, int32_t units_per_group);
 
+/* ---- Action and winding observables of both formulations ---------------------------------------------------
+ * ActionTwoPoint (supervillain/observable/action.py:64-152) and Winding_Winding (winding.py:76-202) are the
+ * autocorrelations Lattice.correlation(a, a) and Lattice.correlation(b, b) of two real fields of one configuration.
+ * They are packed as z = a + i b and share one transform pass: the power-spectrum load unpacks
+ * A(k) = (Z(k) + conj Z(-k)) / 2, B(k) = (Z(k) - conj Z(-k)) / (2i) and loads |A|^2 + i |B|^2, whose transform
+ * carries C_aa in its real and C_bb in its imaginary part.  Off the FFT path one direct sum serves both fields.
+ * path, the size limits and the "not implemented" errors are those of the direct pair above.  Outputs are N*N
+ * float64 each, indexed [dt mod N, dx mod N], with the reference's contact terms applied; either may be NULL.
+ * None of these changes a state or touches an rng; they run on the context's stream. */
+/* The Worldline sums of one configuration, l = m - delta(v) / W_eff.  For integer v and integer W_eff (exact = 1)
+ * W l and d(W l) are formed as int64, their sums of squares are exact and the float sums are those divided once by
+ * W^2; otherwise (exact = 0) the float sums have an order fixed by N and the two w_* sums are 0. */
+typedef struct sv_worldline_sums {
+    double links_squared;    /* sum over links of l^2 */
+    double curl_squared;     /* sum over plaquettes of (d l)^2 */
+    int64_t m0, m1;          /* sum of m_0, of m_1 */
+    int64_t exact;
+    int64_t w_links_squared; /* sum (W l)^2 */
+    int64_t w_curl_squared;  /* sum d(W l)^2 */
+} sv_worldline_sums;
+/* Replaces ActionTwoPoint.Villain (action.py:64-101) on a = kappa/2 (l_0^2 + l_1^2), l = d(phi) - 2 pi n, with
+ * out_action[0] -= mean(a), and Winding_Winding.Villain (winding.py:76-86) on b = d(n).  scalars (4 doubles, may be
+ * NULL): what sv_villain_observables gives for the same state. */
+int sv_villain_action_winding(sv_villain *st, double kappa, double *out_action, double *out_winding, double *scalars,
+                              int32_t path);
+/* Replaces ActionTwoPoint.Worldline (action.py:103-152) on a = 1 - (l_0^2 + l_1^2) / (2 kappa) with
+ * out_action[0] -= sum l^2 / (2 kappa V), and Winding_Winding.Worldline (winding.py:88-202):
+ * (kappa contact - C_bb) / (2 pi kappa)^2 on b = d(l), contact the stencil d(delta(unit source)).  scalars may be
+ * NULL. */
+int sv_worldline_action_winding(sv_worldline *st, double kappa, double W_eff, double *out_action, double *out_winding,
+                                sv_worldline_sums *scalars, int32_t path);
+/* The Worldline sums alone: the counterpart of sv_villain_observables. */
+int sv_worldline_observables(sv_worldline *st, double kappa, double W_eff, sv_worldline_sums *out);
+/* One-shot form on host float64 fields a, b (N*N each; b and out_bb may be NULL): out_aa = Lattice.correlation(a, a),
+ * out_bb = Lattice.correlation(b, b) (compact.py:465-...), no contact terms. */
+int sv_correlation_real(sv_ctx *ctx, int32_t N, const double *a, const double *b, double *out_aa, double *out_bb,
+                        int32_t path);
+
 #ifdef __cplusplus
 }
 #endif

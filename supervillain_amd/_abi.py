@@ -37,6 +37,19 @@ class SvStats(ctypes.Structure):
     ]
 
 
+class SvWorldlineSums(ctypes.Structure):
+    """sv_worldline_sums: the sums of one Worldline configuration, l = m - delta(v) / W (include/supervillain_amd.h)."""
+    _fields_ = [
+        ('links_squared', ctypes.c_double),
+        ('curl_squared', ctypes.c_double),
+        ('m0', ctypes.c_int64),
+        ('m1', ctypes.c_int64),
+        ('exact', ctypes.c_int64),
+        ('w_links_squared', ctypes.c_int64),
+        ('w_curl_squared', ctypes.c_int64),
+    ]
+
+
 class SvMT19937(ctypes.Structure):
     """sv_mt19937: NumPy's legacy global RandomState (MT19937) key and position (include/supervillain_amd.h)."""
     _fields_ = [('key', ctypes.c_uint32 * 624), ('pos', ctypes.c_int32)]

@@ -7,7 +7,7 @@ import logging
 import os
 import threading
 
-from supervillain_amd._abi import SvMT19937, SvPhilox, SvRng, SvStats
+from supervillain_amd._abi import SvMT19937, SvPhilox, SvRng, SvStats, SvWorldlineSums
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsvhip.so')
@@ -141,6 +141,10 @@ def lib():
         L.sv_correlation.argtypes = [vp, i32, vp, vp, i32]
         L.sv_taxicab_correlator.argtypes = [vp, i32, vp, f64, f64, i32, vp]
         L.sv_ctx_set_taxicab_units.argtypes = [vp, i32]
+        L.sv_villain_action_winding.argtypes = [vp, f64, vp, vp, vp, i32]
+        L.sv_worldline_action_winding.argtypes = [vp, f64, f64, vp, vp, P(SvWorldlineSums), i32]
+        L.sv_worldline_observables.argtypes = [vp, f64, f64, P(SvWorldlineSums)]
+        L.sv_correlation_real.argtypes = [vp, i32, vp, vp, vp, vp, i32]
         _LIB = L
         return L
 
@@ -166,7 +170,9 @@ EXPORTED = ('sv_ctx_create', 'sv_ctx_destroy', 'sv_last_error', 'sv_device_count
             'sv_replicas_run', 'sv_replicas_run_measured', 'sv_replicas_villain', 'sv_villain_worm_run', 'sv_replicas_worm_run', 'sv_worldline_worm_run',
             'sv_worldline_worm_batch',
             'sv_villain_spin_spin', 'sv_worldline_vortex_vortex', 'sv_villain_vortex_vortex', 'sv_worldline_spin_spin',
-            'sv_correlation', 'sv_taxicab_correlator', 'sv_ctx_set_taxicab_units')
+            'sv_correlation', 'sv_taxicab_correlator', 'sv_ctx_set_taxicab_units',
+            'sv_villain_action_winding', 'sv_worldline_action_winding', 'sv_worldline_observables',
+            'sv_correlation_real')
 
 
 def default_device():

@@ -186,7 +186,7 @@ class Ensemble:
     def __getattr__(self, name):
         if name == 'configuration':
             raise AttributeError(name)
-        if name in observable.registry and 'Action' in self.__dict__:
+        if name in observable.primary and 'Action' in self.__dict__:
             # an observable (observable/observable.py:36-93): inline column, or measured per configuration and cached
             return observable.measure(self, name)
         return getattr(self.configuration, name)
